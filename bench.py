@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the MI355X path-tracing hot path on BASELINE's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +16,11 @@ the fallback where IPC is refused) — the composite of src/renderer.rs:63-95. N
 barriers and the max over ranks of the timings. `--scaling weak` (opt-in) renders
 the full frame on every rank with disjoint sample ranges instead.
 
-Prints ONE JSON line on rank 0 (metric/value/unit, roofline, cpu_baseline).
+Prints ONE JSON line on rank 0 (metric/value/unit, ms_per_step, the frame's md5). A plain run
+does only that: set up, warm up, time the K steps, print. `--full` adds what takes work of its
+own after the timed steps: the oracle run behind `roofline` (algorithmic bytes per sample, the
+committed PMC summaries) and `cpu_baseline`. `--dump-outputs DIR` writes the last timed step's
+frame and segment count as DIR/*.npy, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -182,6 +186,18 @@ def rank_work(rt, cfg, rank: int, world: int, scaling: str, exact_bvh: bool = Fa
     return params, pixels
 
 
+def dump_outputs(path: str, frame, width: int, height: int, segments_per_step: float) -> None:
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as .npy files under
+    `path`. frame.npy is the frame rank 0 ends with (the render's output buffer on one GPU, the gathered frame
+    on N), float32 [height, width, 3], bit for bit; segments.npy is the segment counter of one step (every
+    timed step renders the same seeded frame, so the counter over the timed steps is `steps` times it).
+    The scene, camera and sample seeds are fixed by the config, so equal arguments give equal inputs."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame.npy"), frame.detach().cpu().numpy().astype(np.float32).reshape(height, width, 3))
+    np.save(os.path.join(path, "segments.npy"), np.array([segments_per_step], dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -200,7 +216,16 @@ def main() -> int:
                     help="frames in flight per rank (three scene handles and streams, RT_FLAG_FRAMES_IN_FLIGHT): "
                          "frame k+1's trace kernel takes the SIMDs frame k's last paths leave, and frame k is "
                          "gathered while frame k+1 renders; auto = on for N>1 (strong scaling), off for one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the oracle (the roofline's algorithmic bytes and "
+                         "cpu_baseline) and quote the committed PMC summaries: adds `roofline` and `cpu_baseline` "
+                         "to the line. Without it the run only sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the last timed step's outputs to DIR: frame.npy (float32, H x W x 3, the "
+                         "gathered frame) and segments.npy (float64, the ray segments one step traced)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -327,7 +352,46 @@ def main() -> int:
         import hashlib
         frame_md5 = hashlib.md5(frame[0].cpu().numpy().tobytes()).hexdigest()
 
+    line = None
     if rank == 0:
+        value = total_samples / wall_max / 1e6
+        line = {
+            # BASELINE.json's metric is quoted on C3; the other configs name their own workload
+            "metric": METRIC if cfg.name == "C3" else
+            f"Msamples/s (rays traced/s) + HBM GB/s vs roofline, {cfg.scene}@{W}x{H}x{spp}spp",
+            "value": value,
+            "unit": "Msamples/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": wall_max / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (seeded scene generator, src/main.rs:559-686 restated)",
+            "config": {"workload": f"{cfg.name} {cfg.scene} {W}x{H} {spp}spp depth {cfg.depth}",
+                       "scene": cfg.scene, "width": W, "height": H, "spp": spp, "max_depth": cfg.depth,
+                       "parallelism": ("weak: full frame per GPU, disjoint sample ranges" if args.scaling == "weak"
+                                       else f"strong: one fixed frame, 8x8 blocks b % {world} == rank per GPU, shards "
+                                            "gathered to rank 0 inside the timed region (rt_shard_pack on every rank, "
+                                            "then rank 0 pulls the peers' IPC-mapped shards over xGMI with "
+                                            "rt_shard_pull_unpack, or the /dev/shm bounce; no collective)" if world > 1
+                                       else "one GPU: the whole frame"),
+                       "gather": gather.transport if gather is not None else None,
+                       "pipeline": ("frames in flight per rank: frame k+1 renders on the next of three scene "
+                                    "handles and streams while frame k drains and is gathered "
+                                    "(RT_FLAG_FRAMES_IN_FLIGHT); every frame is complete and gathered inside the "
+                                    "timed region" if pipeline else None),
+                       "exact_bvh": args.exact_bvh},
+            "rays_per_s": seg_total / wall_max,
+            "segments": int(seg_total),
+            "segments_per_sample": seg_total / total_samples if total_samples else None,
+            "image_finite": img_ok,
+            "frame_sum": frame_sum,
+            "frame_md5": frame_md5,
+        }
+    if rank == 0 and args.full:
         # BASELINE.json config 1 (C1) is the single-thread CPU reference over the whole frame
         c1 = cfg.name == "C1" and args.cpu_threads is None
         threads = 1 if c1 else (args.cpu_threads or cpu_threads())
@@ -367,47 +431,12 @@ def main() -> int:
         valu = pmc_summary("valu", cfg.name, md5) if world == 1 else None
         if valu:
             valu = {k: v for k, v in valu.items() if k != "counters"}
-        value = total_samples / wall_max / 1e6
         bound, bound_why = roofline_bound(valu)
         traffic_gbs = (traffic / (kernel_ms / 1e3) / 1e9) if traffic else None
         if cpu:
             cpu["gpu_over_cpu"] = value / cpu["value"]
             cpu["gpu_over_host_nproc_extrapolation"] = value / cpu["host_nproc_linear_extrapolation"]
-        line = {
-            # BASELINE.json's metric is quoted on C3; the other configs name their own workload
-            "metric": METRIC if cfg.name == "C3" else
-            f"Msamples/s (rays traced/s) + HBM GB/s vs roofline, {cfg.scene}@{W}x{H}x{spp}spp",
-            "value": value,
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": wall_max / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (seeded scene generator, src/main.rs:559-686 restated)",
-            "config": {"workload": f"{cfg.name} {cfg.scene} {W}x{H} {spp}spp depth {cfg.depth}",
-                       "scene": cfg.scene, "width": W, "height": H, "spp": spp, "max_depth": cfg.depth,
-                       "parallelism": ("weak: full frame per GPU, disjoint sample ranges" if args.scaling == "weak"
-                                       else f"strong: one fixed frame, 8x8 blocks b % {world} == rank per GPU, shards "
-                                            "gathered to rank 0 inside the timed region (rt_shard_pack on every rank, "
-                                            "then rank 0 pulls the peers' IPC-mapped shards over xGMI with "
-                                            "rt_shard_pull_unpack, or the /dev/shm bounce; no collective)" if world > 1
-                                       else "one GPU: the whole frame"),
-                       "gather": gather.transport if gather is not None else None,
-                       "pipeline": ("frames in flight per rank: frame k+1 renders on the next of three scene "
-                                    "handles and streams while frame k drains and is gathered "
-                                    "(RT_FLAG_FRAMES_IN_FLIGHT); every frame is complete and gathered inside the "
-                                    "timed region" if pipeline else None),
-                       "exact_bvh": args.exact_bvh},
-            "rays_per_s": seg_total / wall_max,
-            "segments": int(seg_total),
-            "segments_per_sample": seg_total / total_samples if total_samples else None,
-            "image_finite": img_ok,
-            "frame_sum": frame_sum,
-            "frame_md5": frame_md5,
+        line.update({
             "roofline": {"bound": bound, "bound_source": bound_why,
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
@@ -435,7 +464,10 @@ def main() -> int:
                          "bytes_per_sample": b_sample, "impl_bytes_per_sample": IMPL_BYTES_PER_SAMPLE,
                          "samples_per_launch": samples_per_trace_launch},
             "cpu_baseline": cpu,
-        }
+        })
+    if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame[0], W, H, seg_total / args.steps)
         print(json.dumps(line), flush=True)
     if gather is not None:
         gather.close()

@@ -37,7 +37,7 @@ if [ "$PHASE" != bench ]; then
 fi
 if [ "$PHASE" != profiles ]; then
     for c in $CFGS; do
-        run "bench_$c.log" 300 python3 -u bench.py --config "$c"
+        run "bench_$c.log" 300 python3 -u bench.py --full --config "$c"
     done
     run bench_driver_style.log 300 python3 -u bench.py --gpus 1 --steps 20 --warmup 5
     run gpu_tests.log 900 python3 -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread

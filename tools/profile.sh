@@ -29,9 +29,10 @@ step() {  # step <name> <seconds> <cmd...>
         exit $rc
     fi
 }
-B="python3 bench.py --config $CFG --steps 1 --warmup 0 --no-cpu-baseline"
+# --full: tools/valu_roofline.py reads the line's roofline.launches_per_step
+B="python3 bench.py --full --config $CFG --steps 1 --warmup 0 --no-cpu-baseline"
 step bench_trace 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o bench --output-format csv \
-    -- python3 bench.py --config "$CFG" --no-cpu-baseline
+    -- python3 bench.py --full --config "$CFG" --no-cpu-baseline
 step pmc_fetch 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o bench --output-format csv -- $B
 step pmc_write 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o bench --output-format csv -- $B
 step pmc_sq 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS \

@@ -440,7 +440,12 @@ int rt_device_numeric_eval(int op, const double* a, const double* b, double* out
  * in: p[3], out: (u, v); op 3: Sphere::hit's root (sphere.rs:49-103) — in: center[3],
  * radius, origin[3], direction[3], t_min, t_max, out: (hit 1/0, t); op 4: a cube side's
  * quotient (k - o) / d as a BVH cube leaf forms it from the ray's reciprocal (in range: RN(1/d) and
- * Markstein's correction; otherwise the division) — in: k, o, d, out: (that quotient, (k - o) / d). */
+ * Markstein's correction; otherwise the division) — in: k, o, d, out: (that quotient, (k - o) / d);
+ * op 5: the quad tail mode's key, rank and push step of one BVH4 node beside the plain loop's —
+ * in: 40 floats per case (min x[4], min y[4], min z[4], max x[4], max y[4], max z[4], child ids[4] as
+ * bit patterns, origin[3], direction[3], t_min, entry t_max, closest, prunable 0/1, delta, unused),
+ * out: 24 words per case (quad keys[4], plain keys[4], then for the quad step and the plain step: sp,
+ * next node, stack nodes[3], stack keys[3]; both start at sp = 1). */
 int rt_device_kat(int op, const float* in, float* out, uint32_t n);
 
 #ifdef __cplusplus

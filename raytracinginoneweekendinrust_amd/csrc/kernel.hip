@@ -62,7 +62,7 @@ enum ProfRegion : uint32_t {
     kPrRefill = 0, kPrSegment, kPrWorld, kPrRecord, kPrEmit, kPrScatter, kPrMarble, kPrStore,
     kPrChecker, kPrImage, kPrUnitSphere, kPrDielectric, kPrLambert, kPrMetal, kPrIso, kPrLog,
     kPrEntry0 = 16, kPrEntryLast = 43, kPrBvhTrip = 44, kPrLeafTest = 45, kPrBvhSetup = 46, kPrBvhPush = 47,
-    kPrBvhPop = 48, kPrBvhCall = 49, kPrCount = 52
+    kPrBvhPop = 48, kPrBvhCall = 49, kPrQuadIter = 50, kPrQuadRepack = 51, kPrCount = 52
 };
 // traversal mode bits (bvh_hit): kModeExact = RT_FLAG_EXACT_BVH; the rest come
 // from DevParams::tune (rt_set_option(RT_OPT_TUNE), diagnostics / A-B runs).
@@ -88,6 +88,9 @@ constexpr bool kPruneAllExpBuild = false;
 constexpr uint32_t kModeBlocksForward = 1u << 21;
 // W4 (RT_OPT_TUNE, A/B only): the 4-wave instance also for the presets that prefer 3 (below).
 constexpr uint32_t kModeW4 = 1u << 22;
+// Quad tail mode of the sphere / box BVH presets (bvh_quad_tail; RT_OPT_TUNE, A/B only): bits 13-15,
+// 0 = on with up to 16 rays, 1 = off, v = 2..7 = on with at most 2 v rays. Same bits either way.
+constexpr uint32_t kModeQuadShift = 13u, kModeQuadMask = 7u << kModeQuadShift;
 // MbShrink (RT_OPT_TUNE, audit build only): halves the medium-first estimate (world_hit)
 [[maybe_unused]] constexpr uint32_t kModeMbShrink = 1u << 29;
 // The RT_OPT_TUNE bits a build honours. Every bit of the product library leaves the image bits
@@ -96,7 +99,7 @@ constexpr uint32_t kModeW4 = 1u << 22;
 // caller can leave parity through the C ABI (the boundary contract: renderer.rs:42-52 has no knob
 // that changes results). The audit, ablation and A/B builds add their diagnostic bits.
 constexpr uint32_t kTuneExact = kModeNoLeafBoxes | kModeNoPermLds | kModeW3 | kModeNoPretest | kModeReplayRef |
-                                kModeNoStream | kModeBlocksForward | kModeW4 | (15u << 24);
+                                kModeNoStream | kModeBlocksForward | kModeW4 | (15u << 24) | kModeQuadMask;
 constexpr uint32_t kTuneAccepted = kTuneExact
 #if defined(RT_LEAF_AUDIT) || defined(RT_ABLATE)
                                    | kModePruneAllExp
@@ -123,7 +126,16 @@ constexpr uint32_t kAbLeaf2 = 1u << 8, kAbKeys2 = 1u << 9, kAbBvh2 = 1u << 10, k
 #endif
 #ifdef RT_PROFILE_REGIONS
 constexpr uint32_t kProfCopies = 64;  // flush targets spread over blockIdx to keep atomics uncontended
-constexpr uint32_t kProfWords = 3 * kPrCount + 16;  // region triples, then the two visit histograms
+// Live-lane histograms of the BVH loop, per top-level entry (classes 0-7, 8: every later entry) and
+// per bin of lanes (1..16 one bin each, then 17-20, 21-24, .. 61-64): wave cycles of the loop
+// iterations that ran with that many lanes still traversing, the iterations, the quad-mode
+// iterations' cycles and count by live rays, and the bvh_hit calls by lanes active at entry.
+constexpr uint32_t kLiveClasses = 9, kLiveBins = 28, kLiveRows = 5;
+constexpr uint32_t kLiveWords = kLiveClasses * kLiveRows * kLiveBins;
+// region triples, the two visit histograms, the live-lane histograms, then the wave's scratch
+// words (the entry being walked; the open iteration's start clock and bin + 1)
+constexpr uint32_t kProfLive0 = 3 * kPrCount + 16, kProfScratch0 = kProfLive0 + kLiveWords;
+constexpr uint32_t kProfWords = kProfScratch0 + 3;
 __device__ unsigned long long g_prof[kProfCopies * kProfWords];
 // per-wave start / end clock (s_memrealtime, 100 MHz) of the fast kernel's last launch: the
 // ramp at the start and the drain at the end of a launch (tools/region_profile.py --waves)
@@ -157,7 +169,7 @@ __device__ __forceinline__ void prof_init() {
 }
 __device__ __forceinline__ void prof_flush() {
     unsigned long long* dst = g_prof + (blockIdx.x % kProfCopies) * kProfWords;
-    for (uint32_t i = threadIdx.x; i < kProfWords; i += blockDim.x)
+    for (uint32_t i = threadIdx.x; i < kProfScratch0; i += blockDim.x)
         if (prof_lds[i]) atomicAdd(&dst[i], prof_lds[i]);
 }
 #define PROF_T0(name) const uint64_t name = __builtin_amdgcn_s_memtime()
@@ -171,13 +183,47 @@ __device__ __forceinline__ void prof_add(uint32_t region, uint64_t t0) {
         prof_lds[2 * kPrCount + region] += (uint64_t)__popcll(m);
     }
 }
+// The live-lane histograms (kLiveRows rows of kLiveBins per entry class; a block is one wave).
+__device__ __forceinline__ uint32_t live_bin(uint32_t n) { return n <= 16u ? n - 1u : 16u + (n - 17u) / 4u; }  // n in 1..64
+__device__ __forceinline__ unsigned long long* live_row(uint32_t row) {
+    const uint32_t cls = (uint32_t)prof_lds[kProfScratch0];
+    return prof_lds + kProfLive0 + ((cls < kLiveClasses ? cls : kLiveClasses - 1u) * kLiveRows + row) * kLiveBins;
+}
+__device__ __forceinline__ void prof_set_entry(uint32_t e) {
+    if (__lane_id() == (uint32_t)__builtin_ctzll(__ballot(1))) prof_lds[kProfScratch0] = e;
+}
+// A boundary between BVH loop iterations: closes the open iteration into rows `row` (cycles) and
+// row + 1 (iterations) at the bin it was opened with, and opens one with n live lanes (0: none).
+__device__ __forceinline__ void prof_live_iter(uint32_t row, uint32_t n) {
+    const uint64_t now = __builtin_amdgcn_s_memtime();
+    if (__lane_id() == (uint32_t)__builtin_ctzll(__ballot(1))) {
+        const uint32_t open = (uint32_t)prof_lds[kProfScratch0 + 2u];
+        if (open) {
+            unsigned long long* h = live_row(row);
+            h[open - 1u] += now - prof_lds[kProfScratch0 + 1u];
+            h[kLiveBins + open - 1u] += 1u;
+        }
+        prof_lds[kProfScratch0 + 1u] = now;
+        prof_lds[kProfScratch0 + 2u] = n ? live_bin(n) + 1u : 0u;
+    }
+}
+__device__ __forceinline__ void prof_live_call() {  // a bvh_hit call, by the lanes active at its entry
+    const uint64_t m = __ballot(1);
+    if (__lane_id() == (uint32_t)__builtin_ctzll(m)) live_row(4u)[live_bin((uint32_t)__popcll(m))] += 1u;
+}
 #define PROF_INIT() prof_init()
 #define PROF_FLUSH() prof_flush()
+#define PROF_ENTRY(e) prof_set_entry(e)
+#define PROF_LIVE_ITER(row, n) prof_live_iter((row), (n))
+#define PROF_LIVE_CALL() prof_live_call()
 #else
 #define PROF_T0(name) do { } while (0)
 #define PROF_ADD(region, t0) do { } while (0)
 #define PROF_INIT() do { } while (0)
 #define PROF_FLUSH() do { } while (0)
+#define PROF_ENTRY(e) do { } while (0)
+#define PROF_LIVE_ITER(row, n) do { } while (0)
+#define PROF_LIVE_CALL() do { } while (0)
 #endif
 #ifdef RT_LEAF_AUDIT
 // Leaf-box audit (audit build, -DRT_LEAF_AUDIT -> librtamd_audit.so): leaves
@@ -1237,9 +1283,35 @@ constexpr uint32_t kSuspMinTrips = RT_SUSP_MIN_TRIPS;
 #define RT_LEAF_Q 8
 #endif
 
-template <int kKind, uint32_t kF, bool kSusp>
+template <int kKind, uint32_t kF, bool kSusp, uint32_t kMinTrips = kSuspMinTrips>
 RT_DEV bool bvh_run(const DevScene& S, float delta, const f4* wrapper, const Ray& r, V inv, float tmin, float& closest,
                     uint32_t& hit_code, uint32_t* stk, uint32_t mode, Trav& tv, uint32_t susp);
+// Quad tail mode (bvh_quad_tail): once the rays of a bvh_hit call that are still traversing fit the
+// call's host quads, each of them is traversed by the four lanes of a quad, one BVH4 child slot per
+// lane. Compiled into the sphere / box BVH preset with Marble textures (the showcase scene, C3), like
+// kMediumFirst: its 4-wave instance in the product's kernel_mc.hip unit, every instance of that preset
+// in the single-unit diagnostic builds. The preset without Marble (<0, 4, 1>) keeps the plain loop: its
+// instance spilled more with the mode than the register guard's table allows (25 -> 28 VGPRs).
+// The instances that carry the mode pay for its registers in two places, so that they spill no more
+// than before it (tests/golden/kernel_resources.json: 25 VGPRs, 484 SGPRs; with the mode 22 and 479):
+// they read the camera from its device copy at each new sample instead of holding its 21 words in
+// SGPRs (trace_samples, as the flat-list unit does), and their plain loop runs the leaf branch as
+// the inlined function leaf_node_visit, which allocates 8 SGPR spills fewer here than the fragment.
+// RT_OPT_TUNE bits 13-15: 0 the default (on, up to 16 rays), 1 off, v = 2..7 on with at most 2 v rays.
+// RT_QUAD_TAIL=0 builds without it (A/B).
+#ifndef RT_QUAD_TAIL
+#define RT_QUAD_TAIL 1
+#endif
+#if defined(RT_SPLIT_MC) && !defined(RT_INSTANCES_TU)
+constexpr bool kQuadTailUnit = false;  // the product's kernel.hip unit: its instances keep the plain loop
+#else
+constexpr bool kQuadTailUnit = RT_QUAD_TAIL;
+#endif
+template <int kKind, uint32_t kF>
+constexpr bool kQuadTail = kQuadTailUnit && kKind == 0 && kF == (kFBvh | kFMarble);
+template <uint32_t kF>
+RT_DEV void bvh_quad_tail(const DevScene& S, float delta, const f4* wrapper, const Ray& r, V inv, float tmin,
+                          float& closest, uint32_t& hit_code, uint32_t* stk, uint32_t mode, Trav& tv, bool live);
 // Which traversal a ray takes into a BVH (bvh_hit, world_walk, the replay pass).
 // kRayFast: the fast BVH4 traversal is exact for it. Its packed slab test (child_keys4_nf)
 // forms each child's interval with max / min, and those equal aabb.rs:28-41's sequential
@@ -1350,7 +1422,7 @@ RT_DEV bool bvh_hit_nan_tmax(const DevScene& S, const f4* wrapper, const Ray& r,
 #define RT_PEEL_WRAPPER 1
 #endif
 constexpr bool kPeelWrapper = RT_PEEL_WRAPPER;
-template <int kKind, uint32_t kF = kFAll>
+template <int kKind, uint32_t kF = kFAll, bool kTopWalk = false>
 RT_DEV bool bvh_hit(const DevScene& S, float delta, uint32_t root, const Ray& r, float tmin, float& closest,
                     uint32_t& hit_code, uint32_t* stk, uint32_t mode, bool& replay) {
     PROF_T0(pcall);
@@ -1396,6 +1468,7 @@ RT_DEV bool bvh_hit(const DevScene& S, float delta, uint32_t root, const Ray& r,
         }
     }
     PROF_ADD(kPrBvhSetup, psetup);
+    PROF_LIVE_CALL();
     Trav tv{root, 0u, 0u, closest, false, kNoNode};
     if constexpr (kPeelWrapper) {
         // The wrapper's one slot (the root's box, bvh.rs:370) tested outside the loop, from scalar
@@ -1417,7 +1490,23 @@ RT_DEV bool bvh_hit(const DevScene& S, float delta, uint32_t root, const Ray& r,
         const float lo = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, tmin));
         const float hi = __builtin_fminf(__builtin_fminf(tfx, tfy), __builtin_fminf(tfz, closest));
         const float te = lo - (prune ? dmi : 0.0f);
-        if (lo <= hi && te <= (prune ? prune_bound(closest) : kInf)) {
+        if constexpr (kQuadTail<kKind, kF> && kTopWalk) {
+            // The plain loop stops, before a visit, once the lanes still in it fit the call's host
+            // quads (hardware quads whose four lanes are all in this call); bvh_quad_tail finishes
+            // those rays. Every lane of the call is back here then, so the finished ones can host.
+            const uint32_t tq = (mode >> kModeQuadShift) & 7u;
+            const uint64_t m = __ballot(1);
+            const uint32_t nhost = (uint32_t)__popcll(m & (m >> 1) & (m >> 2) & (m >> 3) & 0x1111111111111111ull);
+            const uint32_t cap = tq == 0u ? 16u : 2u * tq;
+            const uint32_t lim = tq == 1u ? 0u : (nhost < cap ? nhost : cap);
+            bool live = false;
+            if (lo <= hi && te <= (prune ? prune_bound(closest) : kInf)) {
+                tv.cur = __float_as_uint(w6.x);
+                live = !bvh_run<kKind, kF, true, 0u>(S, delta, wrapper, r, inv, tmin, closest, hit_code, stk, mode, tv, lim);
+            }
+            if (__ballot(live) != 0ull)
+                bvh_quad_tail<kF>(S, delta, wrapper, r, inv, tmin, closest, hit_code, stk, mode, tv, live);
+        } else if (lo <= hi && te <= (prune ? prune_bound(closest) : kInf)) {
             tv.cur = __float_as_uint(w6.x);
             bvh_run<kKind, kF, false>(S, delta, wrapper, r, inv, tmin, closest, hit_code, stk, mode, tv, 0u);
         }
@@ -1430,6 +1519,14 @@ RT_DEV bool bvh_hit(const DevScene& S, float delta, uint32_t root, const Ray& r,
     return any;
 }
 
+// One leaf node of the fast traversal for the quad tail mode, which runs it on one lane of a quad:
+// bvh_run's own leaf branch (leaf_node_body.inc).
+template <uint32_t kF>
+RT_DEV void leaf_node_visit(const DevScene& S, float delta, uint32_t lnode, uint32_t onx, uint32_t ony, uint32_t onz,
+                            bool leaf_boxes, float tmax_entry, const Ray& r, V inv, float tmin, float& closest,
+                            uint32_t& best_rank, uint32_t& hit_code, bool& any, [[maybe_unused]] uint32_t mode) {
+#include "leaf_node_body.inc"
+}
 // The fast BVH4 traversal loop from state tv: tv.cur is the next node to visit, tv.sp the
 // entries on the lane's stack, tv.tmax_entry the t_max the BVH was entered with (every box
 // test uses it), tv.best_rank / tv.any the best candidate so far (its t in `closest`, its
@@ -1440,12 +1537,9 @@ RT_DEV bool bvh_hit(const DevScene& S, float delta, uint32_t root, const Ray& r,
 // false; the walk resumes it on a later trip of the sample loop, together with the lanes
 // that reach the same BVH then. The visit order and every value are unchanged, only when a
 // visit runs differs, so the result is the same bits.
-#ifndef RT_POP_PREFETCH
-#define RT_POP_PREFETCH 0
-#endif
-template <uint32_t kF>
-constexpr bool kPopPrefetch = RT_POP_PREFETCH && (kF & (kFTri | kFDeep)) == 0u;
-template <int kKind, uint32_t kF, bool kSusp>
+// kMinTrips: the visits a call makes before it may stop (the suspending walk's kSuspMinTrips; 0 for
+// the quad tail mode's hand-over, bvh_hit, which stops before any visit once the wave fits).
+template <int kKind, uint32_t kF, bool kSusp, uint32_t kMinTrips>
 RT_DEV bool bvh_run(const DevScene& S, float delta, const f4* wrapper, const Ray& r, V inv, float tmin, float& closest,
                     uint32_t& hit_code, uint32_t* stk, uint32_t mode, Trav& tv, uint32_t susp) {
     const float tmax_entry = tv.tmax_entry;
@@ -1481,12 +1575,13 @@ RT_DEV bool bvh_run(const DevScene& S, float delta, const f4* wrapper, const Ray
 #endif
     for (;;) {
         if constexpr (kSusp) {
-            if (trips >= kSuspMinTrips && (uint32_t)__popcll(__ballot(1)) <= susp) {
+            if (trips >= kMinTrips && (uint32_t)__popcll(__ballot(1)) <= susp) {
                 finished = false;
                 break;
             }
             ++trips;
         }
+        PROF_LIVE_ITER(0u, (uint32_t)__popcll(__ballot(1)));
         // this trip: test one leaf node (the parked one first), or park the current leaf, or
         // visit the current interior node. Without postponement `cur` is always a node here.
         uint32_t lnode = kNoNode;
@@ -1548,109 +1643,13 @@ RT_DEV bool bvh_run(const DevScene& S, float delta, const f4* wrapper, const Ray
 #ifdef RT_PROFILE_REGIONS
         ++visits;
 #endif
-        // RT_POP_PREFETCH (A/B): the stack top read at the start of the trip, beside the node loads. A trip
-        // that pops has pushed nothing, so the first entry its pop loop takes is this one.
-        [[maybe_unused]] uint32_t pf_node = 0u;
-        [[maybe_unused]] float pf_t = 0.0f;
-        if constexpr (kPopPrefetch<kF>) {
-            const uint32_t top = (sp > 0u ? sp - 1u : 0u) * 128u;
-            pf_node = stk[top];
-            pf_t = __uint_as_float(stk[top + 64u]);
-        }
         PROF_T0(pt);
         if (lnode != kNoNode) {
-            // The 1-2 leaf children of ONE reference BVH2 node, left then right,
-            // and that node's result formed exactly like bvh.rs:377-414: the left
-            // leaf is tested with the BVH's entry t_max, the right one with the
-            // left hit's t (t_max_for_right), and `if left.t < right.t {left} else
-            // {right}`. This matters for f64 spheres: sphere.rs compares its root
-            // against the f32 t_max before rounding t to f32, so a sphere whose
-            // rounded t equals another candidate's passes or fails depending on
-            // which t_max it saw. The node result then joins (closest, DFS rank)
-            // like the tree-min does.
-            const uint32_t nbo = (lnode & ~rtdev::kLeafNodeFlag) * (rtdev::kBvhNodeF4 * 16u);  // node byte offset
-            const f4* nd = S.nodes;
-            const float2 nx2 = ld2_at(nd, nbo + onx), ny2 = ld2_at(nd, nbo + ony), nz2 = ld2_at(nd, nbo + onz),
-                         fx2 = ld2_at(nd, nbo + (onx ^ 48u)), fy2 = ld2_at(nd, nbo + (ony ^ 80u)),
-                         fz2 = ld2_at(nd, nbo + (onz ^ 112u)), chs = ld2_at(nd, nbo + 96u), rks = ld2_at(nd, nbo + 112u);
-            float tmr = tmax_entry, nt = 0.0f;
-            bool nh = false;
-            uint32_t ncode = 0u, nrank = 0u;
-            const uint32_t nleaf = __float_as_uint(chs.y) == rtdev::kChildEmpty ? 1u : 2u;
-            float llo[2] = {-kInf, -kInf}, lhi[2] = {kInf, kInf};
-            if (leaf_boxes) leaf_intervals2_nf(nx2, ny2, nz2, fx2, fy2, fz2, r, inv, delta, llo, lhi);
-            for (uint32_t k = 0; k < nleaf; ++k) {
-                const uint32_t lcode = __float_as_uint(k ? chs.y : chs.x), rank = __float_as_uint(k ? rks.y : rks.x);
-#ifdef RT_LEAF_AUDIT
-                const float2 bx0 = ld2(S.nodes + nbo / 16u, 0), by0 = ld2(S.nodes + nbo / 16u, 1),
-                             bz0 = ld2(S.nodes + nbo / 16u, 2), bx1 = ld2(S.nodes + nbo / 16u, 3),
-                             by1 = ld2(S.nodes + nbo / 16u, 4), bz1 = ld2(S.nodes + nbo / 16u, 5);
-                const float x0 = k ? bx0.y : bx0.x, y0 = k ? by0.y : by0.x, z0 = k ? bz0.y : bz0.x;
-                const float x1 = k ? bx1.y : bx1.x, y1 = k ? by1.y : by1.x, z1 = k ? bz1.y : bz1.x;
-#endif
-                // the right leaf can only matter if t <= min(closest, left t)
-                const float bound = tmr < closest ? tmr : closest;
-                if (!leaf_boxes || leaf_interval_may_hit(k ? llo[1] : llo[0], k ? lhi[1] : lhi[0], tmin, bound)) {
-                    PROF_T0(pl);
-                    // Only candidates whose f32 t can tie or beat closest matter, so
-                    // the test may use min(t_max, nextup(closest)): a root in
-                    // (closest, nextup] is still judged against the reference's own
-                    // t_max, anything beyond rounds above closest and loses anyway.
-                    const float cap = closest < kInf ? __uint_as_float(__float_as_uint(closest) + 1u) : kInf;
-                    float c = tmr < cap ? tmr : cap;
-                    uint32_t code = 0u;
-                    const RayD q = to_d(r);  // f64 ray for sphere leaves, rebuilt here rather than kept live
-                    ABLATE(kAbLeaf2, float c2 = c; uint32_t h2 = 0u;
-                           if (leaf_hit<kF>(S, lcode, r, q, tmin, c2, h2) && h2 == 0x7fffffffu) c = -1.0f;);
-                    // cube sides from the ray's reciprocals (side_t_rcp) except in the triangle preset,
-                    // whose instance lost 1.6% to the extra code (C3 +2%; uniform_entries_ab.log)
-                    bool hit;
-                    if constexpr (kLeafEmbed<kF>) {
-                        const uint32_t ltype = rtdev::leaf_type(lcode);
-                        // leaf k's lane of rows 0-6 (the node's line, just fetched; the address needs
-                        // no record index, so the loads do not wait on the child row)
-                        const uint32_t lo = nbo + 4u * k;
-                        if (ltype == rtdev::kLeafSphere) {  // (cx, cy, cz, r) in lane 2 + k of rows 0, 1, 2, 6
-                            const f4 sp{ld1_at(nd, lo + 8u), ld1_at(nd, lo + 24u), ld1_at(nd, lo + 40u), ld1_at(nd, lo + 104u)};
-                            float ts;
-                            hit = sphere_t(sp, q, tmin, c, ts);
-                            if (hit) {
-                                c = ts;
-                                code = lcode;
-                            }
-                        } else if (ltype == rtdev::kLeafCube) {  // its leaf box (lane k of rows 0-5) is its bounds
-                            hit = cube_hit<(kF & kFTri) == 0u>(S, rtdev::leaf_index(lcode), ld1_at(nd, lo), ld1_at(nd, lo + 16u),
-                                                               ld1_at(nd, lo + 32u), ld1_at(nd, lo + 48u), ld1_at(nd, lo + 64u),
-                                                               ld1_at(nd, lo + 80u), r, inv, tmin, c, code);
-                        } else {
-                            hit = leaf_hit<kF, (kF & kFTri) == 0u, false, true>(S, lcode, r, q, tmin, c, code, inv);
-                        }
-                    } else {
-                        hit = leaf_hit<kF, (kF & kFTri) == 0u>(S, lcode, r, q, tmin, c, code, inv);
-                    }
-                    if (hit) {
-                        // cube faces rank + 0..5 (the face leaf_hit's list walk kept)
-                        const uint32_t rk = rank + (rtdev::leaf_type(lcode) == rtdev::kLeafCube
-                                                        ? rtdev::leaf_index(code) - rtdev::leaf_index(lcode)
-                                                        : 0u);
-                        if (!nh || !(nt < c)) {
-                            nh = true;
-                            nt = c;
-                            ncode = code;
-                            nrank = rk;
-                        }
-                        tmr = c;
-                    }
-                    PROF_ADD(kPrLeafTest, pl);
-                } else {
-                    LEAF_AUDIT(lcode, rank, x0, y0, z0, x1, y1, z1);
-                }
-            }
-            if (nh && (nt < closest || (nt == closest && nrank > best_rank))) {
-                closest = nt;
-                best_rank = nrank;
-                hit_code = ncode;
-                any = true;
+            if constexpr (kQuadTail<kKind, kF>) {
+                leaf_node_visit<kF>(S, delta, lnode, onx, ony, onz, leaf_boxes, tmax_entry, r, inv, tmin, closest,
+                                    best_rank, hit_code, any, mode);
+            } else {
+#include "leaf_node_body.inc"
             }
         }
         float t0 = kInf, t1 = kInf, t2 = kInf, t3 = kInf;
@@ -1722,16 +1721,11 @@ RT_DEV bool bvh_run(const DevScene& S, float delta, const f4* wrapper, const Ray
         PROF_T0(ppop);
         if (popnext) {
             bool found = false;
-            [[maybe_unused]] bool first = true;
             while (sp > 0u) {
                 sp -= 1u;
                 uint32_t cand;
                 float tenter;
-                if (kPopPrefetch<kF> && first) {
-                    cand = pf_node;
-                    tenter = pf_t;
-                    first = false;
-                } else if (!(kF & kFDeep) || sp < S.stack_depth) {
+                if (!(kF & kFDeep) || sp < S.stack_depth) {
                     cand = stk[sp * 128u];
                     tenter = __uint_as_float(stk[sp * 128u + 64u]);
                 } else {
@@ -1761,6 +1755,7 @@ RT_DEV bool bvh_run(const DevScene& S, float delta, const f4* wrapper, const Ray
         }
     }
     tv = Trav{cur, sp, best_rank, tmax_entry, any, pend};
+    PROF_LIVE_ITER(0u, 0u);
 #ifdef RT_PROFILE_REGIONS
     {
         const uint32_t b = trips_bin(visits);
@@ -1778,6 +1773,211 @@ RT_DEV bool bvh_run(const DevScene& S, float delta, const f4* wrapper, const Ray
     }
 #endif
     return finished;
+}
+
+// ---------------------------------------------------------------------------
+// Quad tail mode: four lanes per ray, one BVH4 child slot per lane (bvh_quad_tail).
+// ---------------------------------------------------------------------------
+// DPP quad_perm: lane i of every hardware quad reads lane (kCtrl >> 2 i) & 3 of its quad.
+constexpr int kQuadRot1 = 0x39, kQuadRot2 = 0x4e, kQuadRot3 = 0x93, kQuadLane0 = 0x00, kQuadXor1 = 0xb1;
+template <int kCtrl>
+RT_DEV uint32_t quad_perm(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, 0xf, 0xf, false);
+}
+template <int kCtrl>
+RT_DEV float quad_perm(float v) {
+    return __uint_as_float(quad_perm<kCtrl>(__float_as_uint(v)));
+}
+// One slot of child_keys4_nf: the same correctly rounded operations on one element (v_sub_f32 /
+// v_mul_f32 for the packed forms), on the slot's six sign-ordered planes.
+RT_DEV float quad_child_key(float nx, float ny, float nz, float fx, float fy, float fz, const Ray& r, V inv, float tmin,
+                            float tmax_entry, float pb, float dmi) {
+    const float tnx = (nx - r.o.x) * inv.x, tfx = (fx - r.o.x) * inv.x;
+    const float tny = (ny - r.o.y) * inv.y, tfy = (fy - r.o.y) * inv.y;
+    const float tnz = (nz - r.o.z) * inv.z, tfz = (fz - r.o.z) * inv.z;
+    const float lo = __builtin_fmaxf(__builtin_fmaxf(tnx, tny), __builtin_fmaxf(tnz, tmin));
+    const float hi = __builtin_fminf(__builtin_fminf(tfx, tfy), __builtin_fminf(tfz, tmax_entry));
+    const float te = lo - dmi;
+    const bool go = lo <= hi && te <= pb;
+    return go ? __builtin_fminf(te, 3.4028235e38f) : kInf;
+}
+// The quad's sort and push. Lane k (its lane & 3) holds slot k's key and child; `sp` and the stack
+// column `qs` are the same in the quad's four lanes. Each lane ranks its key among the quad's (ties:
+// the lower slot first), the lane of each visited child but the nearest writes its own {node, t}
+// entry, far to near from sp up, and the nearest child becomes every lane's `cur`. Returns false,
+// with nothing written, when no child is visited.
+// Tie order: bvh_run's 5-comparator network is not a stable sort and no fixed rule between two
+// slots reproduces its permutation of equal keys (slots 0 and 1 swap or not depending on slot 3),
+// so children with equal keys may be visited in another order than in the plain loop. The result
+// does not depend on the visit order.
+RT_DEV bool quad_sort_push(float key, uint32_t child, uint32_t k, uint32_t* qs, uint32_t& sp, uint32_t& cur) {
+    // rotation r brings slot (k + r) & 3, the lower slot when k + r >= 4
+    const float k1 = quad_perm<kQuadRot1>(key), k2 = quad_perm<kQuadRot2>(key), k3 = quad_perm<kQuadRot3>(key);
+    const uint32_t rank = ((k1 < key || (k1 == key && k >= 3u)) ? 1u : 0u) + ((k2 < key || (k2 == key && k >= 2u)) ? 1u : 0u) +
+                          ((k3 < key || (k3 == key && k >= 1u)) ? 1u : 0u);
+    const uint32_t others = (k1 != kInf ? 1u : 0u) + (k2 != kInf ? 1u : 0u) + (k3 != kInf ? 1u : 0u);
+    const bool vis = key != kInf;
+    if (vis && rank != 0u) {  // ranks 1 .. n - 1 at sp + n - 1 - rank (n - 1 = others for a visited slot)
+        const uint32_t at = (sp + others - rank) * 128u;
+        qs[at] = child;
+        qs[at + 64u] = __float_as_uint(key);
+    }
+    uint32_t nearest = vis && rank == 0u ? child : 0u;
+    nearest |= quad_perm<kQuadXor1>(nearest);
+    nearest |= quad_perm<kQuadRot2>(nearest);
+    const uint32_t n = others + (vis ? 1u : 0u);
+    if (n == 0u) return false;
+    cur = nearest;
+    sp += n - 1u;
+    return true;
+}
+[[maybe_unused]] __shared__ uint32_t quad_map[32];  // bvh_quad_tail's lane maps (a block is one wave)
+#ifdef RT_LEAF_AUDIT
+__device__ unsigned long long g_quad_iters;  // quad-mode loop iterations (rays x iterations), audit build
+#endif
+// The tail of a bvh_hit call's traversals. On entry every lane of the call is here; `live` lanes
+// hold a traversal the plain loop stopped (bvh_run, state in tv / closest / hit_code, stack in the
+// lane's LDS column), at most as many as the call has host quads (hardware quads with all four lanes
+// in the call). Live ray j (by lane order) is traversed by host quad j:
+// * repack, once: the quad's lanes fetch the ray and its traversal state from the owner lane
+//   (ds_bpermute); the owner's stack stays where it is, the quad addresses that column. A host lane's
+//   own values (a finished traversal's result, or a live state that another quad now runs) stay in
+//   its own variables;
+// * iteration: an interior node's four slots are tested one per lane (quad_child_key), ranked and
+//   pushed across the quad (quad_sort_push); a leaf node runs on the quad's lane 0 with bvh_run's own
+//   leaf code and its result is shared; the pop loop runs in all four lanes on the same column
+//   (broadcast reads). The four lanes hold the same state and take the same branches; the loop ends
+//   on a wave ballot;
+// * unpack: each owner reads closest, the hit and the DFS rank from lane 0 of its host quad.
+// Every key, prune decision, leaf test and merge is bvh_run's, so the result is the same bits;
+// equal keys may be visited in another order (quad_sort_push).
+template <uint32_t kF>
+RT_DEV void bvh_quad_tail(const DevScene& S, float delta, const f4* wrapper, const Ray& r, V inv, float tmin,
+                          float& closest, uint32_t& hit_code, uint32_t* stk, uint32_t mode, Trav& tv, bool live) {
+    PROF_T0(prep);
+    const uint32_t lane = __lane_id(), k = lane & 3u;
+    const uint64_t m = __ballot(1), L = __ballot(live);
+    const uint64_t H = m & (m >> 1) & (m >> 2) & (m >> 3) & 0x1111111111111111ull;  // lane 0 of each host quad
+    const uint32_t nlive = (uint32_t)__popcll(L);
+    const auto below = [](uint64_t x) {  // set bits of x below this lane
+        return __builtin_amdgcn_mbcnt_hi((uint32_t)(x >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)x, 0u));
+    };
+    const auto pull = [](uint32_t from, uint32_t v) {
+        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(from << 2), (int)v);
+    };
+    const auto pullf = [&](uint32_t from, float v) { return __uint_as_float(pull(from, __float_as_uint(v))); };
+    // the two maps, through quad_map (the wave's own words; LDS operations of one wave run in order):
+    // [j] = the lane of live ray j, [16 + j] = lane 0 of host quad j
+    const uint32_t live_rank = below(L), h0_rank = below(H);
+    const bool h0 = ((uint32_t)(H >> lane) & 1u) != 0u;
+    if (live && live_rank < 16u) quad_map[live_rank] = lane;
+    if (h0 && h0_rank < 16u) quad_map[16u + h0_rank] = lane;
+    __builtin_amdgcn_wave_barrier();
+    const bool host_quad = ((uint32_t)(H >> (lane & 60u)) & 1u) != 0u;
+    const uint32_t hq = below(H << 3);  // this quad's index among the host quads (every lane of the quad)
+    const bool hosting = host_quad && hq < nlive && hq < 16u;
+    const uint32_t owner = hosting ? (quad_map[hq & 15u] & 63u) : lane;
+    // live lanes: lane 0 of the quad that runs my ray (kNoNode: this lane holds no live ray). The per-lane
+    // flags of the loop live in vector registers (cur == kNoNode: this lane hosts nothing or its ray has
+    // finished; any_u), not in lane masks: scalar registers are the scarce ones in these instances.
+    const uint32_t my_host = live ? (quad_map[16u + (live_rank & 15u)] & 63u) : kNoNode;
+    __builtin_amdgcn_wave_barrier();
+    // the hosted ray and its traversal state
+    Ray q;
+    q.o = mk(pullf(owner, r.o.x), pullf(owner, r.o.y), pullf(owner, r.o.z));
+    q.d = mk(pullf(owner, r.d.x), pullf(owner, r.d.y), pullf(owner, r.d.z));
+    q.time = (kF & kFLeafRM) != 0u ? pullf(owner, r.time) : 0.0f;
+    const V qi = mk(pullf(owner, inv.x), pullf(owner, inv.y), pullf(owner, inv.z));
+    float qc = pullf(owner, closest);
+    const float qtmax = pullf(owner, tv.tmax_entry);
+    uint32_t cur = pull(owner, tv.cur), sp = pull(owner, tv.sp), brank = pull(owner, tv.best_rank);
+    uint32_t hcode = pull(owner, hit_code);
+    uint32_t any_u = pull(owner, tv.any ? 1u : 0u);
+    if (!hosting) cur = kNoNode;
+    uint32_t* qs = stk + owner - lane;  // the owner's stack column
+    const bool prune = (__float_as_uint(ld4c(wrapper + 7).w) & rtdev::kBvhPrunable) != 0u ||
+                       (kPruneAllExpBuild && (mode & kModePruneAllExp));
+    const float dmi = delta * fmaxf(fmaxf(__builtin_fabsf(qi.x), __builtin_fabsf(qi.y)), __builtin_fabsf(qi.z));
+    PROF_ADD(kPrQuadRepack, prep);
+    [[maybe_unused]] uint32_t iters = 0u;
+    for (;;) {
+        const bool alive = cur != kNoNode;
+        const uint64_t am = __ballot(alive);
+        if (am == 0ull) break;
+        PROF_LIVE_ITER(2u, (uint32_t)__popcll(am) / 4u);
+        PROF_T0(pq);
+#ifdef RT_LEAF_AUDIT
+        if (alive && k == 0u) iters += 1u;
+        if (alive && ((cur & ~rtdev::kLeafNodeFlag) >= S.num_nodes || sp > S.stack_depth + S.spill_depth)) {
+            atomicAdd(&g_bounds_audit_count, 1u);
+            cur = kNoNode;
+            continue;
+        }
+#endif
+        uint32_t msx, msy, msz;
+        asm volatile("v_ashrrev_i32 %0, 31, %1" : "=v"(msx) : "v"(qi.x));
+        asm volatile("v_ashrrev_i32 %0, 31, %1" : "=v"(msy) : "v"(qi.y));
+        asm volatile("v_ashrrev_i32 %0, 31, %1" : "=v"(msz) : "v"(qi.z));
+        const uint32_t onx = msx & 48u, ony = (msy & 48u) + 16u, onz = (msz & 48u) + 32u;
+        const bool leaf = alive && (cur & rtdev::kLeafNodeFlag) != 0u;
+        if (__ballot(leaf) != 0ull) {
+            if (leaf && k == 0u) {
+                bool qany = any_u != 0u;
+                leaf_node_visit<kF>(S, delta, cur, onx, ony, onz, prune && !(mode & kModeNoLeafBoxes), qtmax, q, qi, tmin,
+                                    qc, brank, hcode, qany, mode);
+                any_u = qany ? 1u : 0u;
+            }
+            qc = quad_perm<kQuadLane0>(qc);
+            brank = quad_perm<kQuadLane0>(brank);
+            hcode = quad_perm<kQuadLane0>(hcode);
+            any_u = quad_perm<kQuadLane0>(any_u);
+        }
+        float key = kInf;
+        uint32_t child = rtdev::kChildEmpty;
+        if (alive && !leaf) {
+            const uint32_t nbo = cur * (rtdev::kBvhNodeF4 * 16u) + 4u * k;  // slot k's lane of the node's rows
+            const f4* nd = S.nodes;
+            const float nx = ld1_at(nd, nbo + onx), ny = ld1_at(nd, nbo + ony), nz = ld1_at(nd, nbo + onz),
+                        fx = ld1_at(nd, nbo + (onx ^ 48u)), fy = ld1_at(nd, nbo + (ony ^ 80u)),
+                        fz = ld1_at(nd, nbo + (onz ^ 112u));
+            child = __float_as_uint(ld1_at(nd, nbo + 96u));
+            key = quad_child_key(nx, ny, nz, fx, fy, fz, q, qi, tmin, qtmax, prune ? prune_bound(qc) : kInf,
+                                 prune ? dmi : 0.0f);
+        }
+        uint32_t next = kNoNode;  // (a quad with lanes outside the call ranks garbage: only hosting quads take it)
+        const bool went = quad_sort_push(key, child, k, qs, sp, next);
+        if (alive) {
+            if (!went) {  // the plain pop loop; nothing left: the ray has finished
+                while (sp > 0u) {
+                    sp -= 1u;
+                    const uint32_t cand = qs[sp * 128u];
+                    const float tenter = __uint_as_float(qs[sp * 128u + 64u]);
+                    if (!prune || !(tenter > prune_bound(qc))) {
+                        next = cand;
+                        break;
+                    }
+                }
+            }
+            cur = next;
+        }
+        PROF_ADD(kPrQuadIter, pq);
+    }
+    PROF_LIVE_ITER(2u, 0u);
+    PROF_T0(pun);
+#ifdef RT_LEAF_AUDIT
+    if (iters) atomicAdd(&g_quad_iters, (unsigned long long)iters);
+#endif
+    // unpack: the owners take their results from lane 0 of their host quads
+    const float rc = pullf(my_host, qc);
+    const uint32_t rh = pull(my_host, hcode), rb = pull(my_host, brank), ra = pull(my_host, any_u);
+    if (my_host != kNoNode) {
+        closest = rc;
+        hit_code = rh;
+        tv.best_rank = rb;
+        tv.any = ra != 0u;
+        tv.sp = 0u;
+    }
+    PROF_ADD(kPrQuadRepack, pun);
 }
 
 // Translate (instance.rs:39) / RotateY (instance.rs:104-110, 121-124) applied to a ray.
@@ -1839,7 +2039,7 @@ constexpr uint32_t kRunPretestMin = 8u;  // sphere runs at least this long take 
 // A GEOM or BVH entry (the caller guarantees E is wave-uniform). Only instances
 // with kFRuns carry the f32 pretest of long sphere runs, only those with kFBvh the
 // BVH traversal (the host launches an instance whose features cover the scene's).
-template <int kKind, uint32_t kF>
+template <int kKind, uint32_t kF, bool kTopWalk = false>
 RT_DEV bool entry_geom_hit(const DevScene& S, float delta, const DevEntry* E, Ray r, float tmin, float& closest,
                            uint32_t& hit_code, uint32_t* stk, uint32_t mode, bool& replay) {
     uint32_t ntf = uni<kF>(cst(E)->ntf);
@@ -1915,8 +2115,8 @@ RT_DEV bool entry_geom_hit(const DevScene& S, float delta, const DevEntry* E, Ra
             ABLATE(kAbBvh2, float c2 = closest; uint32_t h2 = 0u; bool rp = false;
                    if (bvh_hit<kKind, kF>(S, delta, cst(E)->payload, r, tmin, c2, h2, stk, mode, rp) && h2 == 0x7fffffffu)
                        closest = -1.0f;);
-            return bvh_hit<kKind, kF>(S, delta, uni<kF>(cst(E)->payload), r, tmin, closest, hit_code, stk, mode,
-                                            replay);
+            return bvh_hit<kKind, kF, kTopWalk>(S, delta, uni<kF>(cst(E)->payload), r, tmin, closest, hit_code, stk, mode,
+                                                replay);
         }
     }
     if constexpr (kUniformEntries<kF>) {
@@ -2550,6 +2750,7 @@ RT_DEV bool world_hit(const DevScene& S, float delta, const Ray& r, Rng& g, cons
     for (uint32_t e = 0; e < S.num_top; ++e) {
         const DevEntry* E = S.entries + e;
         PROF_T0(pe);
+        PROF_ENTRY(e);
         if (uni<kF>(cst(E)->kind) == rtdev::kEntMedium) {
             float t, vb = kInf;
             if constexpr (kKind == 0 && kMediumFirst<kF>) {
@@ -2569,7 +2770,7 @@ RT_DEV bool world_hit(const DevScene& S, float delta, const Ray& r, Rng& g, cons
             }
         } else {
             uint32_t code;
-            if (entry_geom_hit<kKind, kF>(S, delta, E, r, 0.001f, closest, code, stk, mode, replay)) {
+            if (entry_geom_hit<kKind, kF, true>(S, delta, E, r, 0.001f, closest, code, stk, mode, replay)) {
                 hit_entry = e;
                 hit_code = code;
                 any = true;
@@ -2603,6 +2804,7 @@ RT_DEV void world_walk(const DevScene& S, float delta, const Ray& ray, Rng& g, c
     for (uint32_t e = 0; e < S.num_top; ++e) {
         if (!(active && w.pos == e)) continue;
         PROF_T0(pe);
+        PROF_ENTRY(e);
         const DevEntry* E = S.entries + e;
         const uint32_t kind = uni<kF>(cst(E)->kind);
         if (kind == rtdev::kEntMedium) {
@@ -3086,7 +3288,9 @@ __global__ __launch_bounds__(64, kWaves) void trace_samples(DevScene Sg, DevCame
     // C3, C4; profiles/r04/experiments/camera_in_memory_ab_*.log).
     const DevCamera& Cs = *reinterpret_cast<const DevCamera*>(reinterpret_cast<const char*>(ctr) + kCamOffset);
 #else
-    const DevCamera& Cs = C;
+    // (the quad tail mode's instances read it from the device copy too: their SGPR budget, kQuadTail)
+    const DevCamera& Cs =
+        kQuadTail<kKind, kF> ? *reinterpret_cast<const DevCamera*>(reinterpret_cast<const char*>(ctr) + kCamOffset) : C;
 #endif
     // item source: the chunk's block batches, or (fixup) the replay list
     unsigned* counter = &ctr->batch;
@@ -3355,6 +3559,88 @@ __global__ void kat_eval(int op, const float* __restrict__ in, float* __restrict
     }
     out[2u * i] = r0;
     out[2u * i + 1u] = r1;
+}
+
+// rt_device_kat op 5: the quad tail mode's key, rank and push step (quad_child_key, quad_sort_push)
+// on 16 quads a block, one case a quad, beside bvh_run's own step (child_keys4_nf, the sort network,
+// the pushes) on the quad's lane 0. A case is 40 floats: the node's min x / y / z and max x / y / z rows
+// (4 slots each), its child row (bit patterns), the ray's origin and direction, t_min, the entry
+// t_max, closest, prunable (0 / 1), delta, one unused. Both start with one entry on the stack (sp = 1).
+// Out, 24 words a case: the quad's four keys, the plain step's four keys, then for the quad and for the
+// plain step eight words each: sp after the step, the next node (~0: no child visited), the nodes
+// and the keys of stack entries 1-3 (0xdeadbeef where nothing was written).
+__global__ __launch_bounds__(64) void kat_quad(const float* __restrict__ in, float* __restrict__ out, uint32_t n) {
+    __shared__ uint32_t ks[2u * 4u * 128u];
+    const uint32_t lane = threadIdx.x, k = lane & 3u, cs = blockIdx.x * 16u + lane / 4u;
+    if (cs >= n) return;  // (whole quads)
+    const float* a = in + 40u * cs;
+    uint32_t* o = reinterpret_cast<uint32_t*>(out) + 24u * cs;
+    Ray r;
+    r.o = mk(a[28], a[29], a[30]);
+    r.d = mk(a[31], a[32], a[33]);
+    r.time = 0.0f;
+    const V inv = mk(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
+    const float tmin = a[34], tmax_entry = a[35], closest = a[36], delta = a[38];
+    const bool prune = a[37] != 0.0f;
+    const float dmi = delta * fmaxf(fmaxf(__builtin_fabsf(inv.x), __builtin_fabsf(inv.y)), __builtin_fabsf(inv.z));
+    const float pb = prune ? prune_bound(closest) : kInf, dm = prune ? dmi : 0.0f;
+    const uint32_t sx = inv.x < 0.0f ? 12u : 0u, sy = inv.y < 0.0f ? 12u : 0u, sz = inv.z < 0.0f ? 12u : 0u;
+    for (uint32_t i = 0; i < 8u; ++i) {
+        ks[i * 128u + lane] = 0xdeadbeefu;
+        ks[i * 128u + 64u + lane] = 0xdeadbeefu;
+    }
+    __builtin_amdgcn_wave_barrier();
+    {
+        const float key = quad_child_key(a[sx + k], a[4u + sy + k], a[8u + sz + k], a[12u - sx + k], a[16u - sy + k],
+                                         a[20u - sz + k], r, inv, tmin, tmax_entry, pb, dm);
+        uint32_t sp = 1u, cur = 0xffffffffu;
+        uint32_t* qs = ks + (lane & 60u);
+        const bool went = quad_sort_push(key, __float_as_uint(a[24u + k]), k, qs, sp, cur);
+        __builtin_amdgcn_wave_barrier();
+        o[k] = __float_as_uint(key);
+        if (k == 0u) {
+            o[8] = sp;
+            o[9] = went ? cur : 0xffffffffu;
+            for (uint32_t i = 0; i < 3u; ++i) {
+                o[10u + i] = qs[(1u + i) * 128u];
+                o[13u + i] = qs[(1u + i) * 128u + 64u];
+            }
+        }
+    }
+    if (k == 0u) {  // bvh_run's interior trip, sort and pushes
+        const auto row = [&](uint32_t b) { return f4{a[b], a[b + 1u], a[b + 2u], a[b + 3u]}; };
+        float key[4];
+        child_keys4_nf(row(sx), row(4u + sy), row(8u + sz), row(12u - sx), row(16u - sy), row(20u - sz), r, inv, tmin,
+                       tmax_entry, pb, dm, key);
+        float t0 = key[0], t1 = key[1], t2 = key[2], t3 = key[3];
+        uint32_t c0 = __float_as_uint(a[24]), c1 = __float_as_uint(a[25]), c2 = __float_as_uint(a[26]),
+                 c3 = __float_as_uint(a[27]);
+        for (uint32_t i = 0; i < 4u; ++i) o[4u + i] = __float_as_uint(key[i]);
+        uint32_t sp = 1u, cur = 0xffffffffu;
+        uint32_t* stk = ks + 512u + lane;
+        auto push = [&](uint32_t node, float t) {
+            stk[sp * 128u] = node;
+            stk[sp * 128u + 64u] = __float_as_uint(t);
+            sp += 1u;
+        };
+        sort2(t0, c0, t1, c1);
+        sort2(t2, c2, t3, c3);
+        sort2(t0, c0, t2, c2);
+        sort2(t1, c1, t3, c3);
+        sort2(t1, c1, t2, c2);
+        if (t0 != kInf) {
+            if (t3 != kInf) push(c3, t3);
+            if (t2 != kInf) push(c2, t2);
+            if (t1 != kInf) push(c1, t1);
+            cur = c0;
+        }
+        o[16] = sp;
+        o[17] = cur;
+        for (uint32_t i = 0; i < 3u; ++i) {
+            o[18u + i] = stk[(1u + i) * 128u];
+            o[21u + i] = stk[(1u + i) * 128u + 64u];
+        }
+    }
 }
 
 }  // namespace
@@ -3727,6 +4013,17 @@ int rt_scene_free(rt_scene_handle s) {
             fprintf(stderr, "]}\n");
         }
         {
+            // per entry class: [cycles, iterations, quad cycles, quad iterations, calls] x kLiveBins
+            fprintf(stderr, "{\"live_hist\": {\"bins\": %u, \"rows\": %u, \"classes\": [", kLiveBins, kLiveRows);
+            for (uint32_t c = 0; c < kLiveClasses; ++c) {
+                fprintf(stderr, "%s[", c ? "," : "");
+                for (uint32_t i = 0; i < kLiveRows * kLiveBins; ++i)
+                    fprintf(stderr, "%s%llu", i ? "," : "", h[kProfLive0 + c * kLiveRows * kLiveBins + i]);
+                fprintf(stderr, "]");
+            }
+            fprintf(stderr, "]}}\n");
+        }
+        {
             const unsigned long long* th = h + 3u * kPrCount;
             fprintf(stderr, "{\"trips_hist\": [%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu], \"wave_max_hist\": "
                             "[%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu]}\n",
@@ -3818,6 +4115,9 @@ int rt_scene_free(rt_scene_handle s) {
         }
         if (hipMemcpyFromSymbol(&na, HIP_SYMBOL(g_bounds_audit_count), sizeof na) == hipSuccess)
             fprintf(stderr, "{\"bounds_audit_count\": %u}\n", na);
+        unsigned long long nq = 0;  // quad tail mode iterations since the library was loaded (bvh_quad_tail)
+        if (hipMemcpyFromSymbol(&nq, HIP_SYMBOL(g_quad_iters), sizeof nq) == hipSuccess)
+            fprintf(stderr, "{\"quad_iters\": %llu}\n", nq);
 #endif
         if (s->done) (void)hipEventSynchronize(s->done);  // the last launch may still use the buffers below
         if (s->pool) (void)hipFree(s->pool);
@@ -4452,20 +4752,24 @@ int rt_prof_rows(uint32_t r0, uint32_t r1) {
 int rt_device_kat(int op, const float* in, float* out, uint32_t n) {
     rthost::clear_error();
     if (!in || !out) return rthost::set_error(RT_ERR_INVALID, "NULL argument");
-    if (op < 0 || op > 4) return rthost::set_error(RT_ERR_INVALID, "unknown KAT op");
+    if (op < 0 || op > 5) return rthost::set_error(RT_ERR_INVALID, "unknown KAT op");
     int rc = check_device(0);
     if (rc) return rc;
     if (n == 0) return RT_OK;
     DeviceGuard g(0);
-    const size_t in_floats = (size_t)n * (op <= 1 ? 14u : (op == 2 || op == 4 ? 3u : 12u)),
-                 out_floats = (size_t)n * 2u;
+    // (op 5, kat_quad: 40 floats in and 24 words out a case)
+    const size_t in_floats = (size_t)n * (op == 5 ? 40u : op <= 1 ? 14u : (op == 2 || op == 4 ? 3u : 12u)),
+                 out_floats = (size_t)n * (op == 5 ? 24u : 2u);
     float *din = nullptr, *dout = nullptr;
     hipError_t e = hipMalloc(&din, in_floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&dout, out_floats * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(din, in, in_floats * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         (void)hipGetLastError();
-        hipLaunchKernelGGL(kat_eval, dim3((n + 63u) / 64u), dim3(64), 0, nullptr, op, din, dout, n);
+        if (op == 5)
+            hipLaunchKernelGGL(kat_quad, dim3((n + 15u) / 16u), dim3(64), 0, nullptr, din, dout, n);
+        else
+            hipLaunchKernelGGL(kat_eval, dim3((n + 63u) / 64u), dim3(64), 0, nullptr, op, din, dout, n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, dout, out_floats * sizeof(float), hipMemcpyDeviceToHost);

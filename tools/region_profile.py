@@ -24,7 +24,7 @@ NAMES = ["Refill", "Finish segment", "World", "Record", "Emit", "Scatter", "Marb
          "UnitSphere", "Dielectric", "Lambert", "Metal", "Isotropic", "MediumLog"]
 COUNT = 52
 EXTRA = {44: "BVH loop trip (child tests)", 45: "BVH leaf test", 46: "BVH call setup", 47: "BVH sort + push",
-         48: "BVH pop loop", 49: "BVH call total"}
+         48: "BVH pop loop", 49: "BVH call total", 50: "Quad tail iteration", 51: "Quad tail repack + unpack"}
 ENTRY0 = 16
 # showcase's top-level entries after lowering (lower.cpp merges consecutive top-level spheres into runs)
 SHOWCASE = ["boxes BVH", "light rect", "moving sphere", "sphere run (glass, metal, medium boundary)",
@@ -81,7 +81,9 @@ def main():
         captured = tf.read().splitlines()
         lines = [ln for ln in captured if ln.startswith('{"rt_profile"')]
         for ln in captured:
-            if ln.startswith(('{"leaf_audit', '{"audit', '{"trav_audit', '{"bounds_audit', '{"trips_hist', '{"wave_times', '{"tp_gseg', '{"role_ev')):
+            if ln.startswith('{"live_hist'):
+                live_table(json.loads(ln)["live_hist"])
+            if ln.startswith(('{"leaf_audit', '{"audit', '{"trav_audit', '{"bounds_audit', '{"quad_iters', '{"trips_hist', '{"wave_times', '{"tp_gseg', '{"role_ev')):
                 print(ln)
     if not lines:  # an audit build: no region counters
         return
@@ -104,6 +106,32 @@ def main():
     print(json.dumps({"band": args.rows, "trace_ms": ms, "segments": segments, "wave_cycles": total,
                       "regions": {name: {"cyc": cyc[i], "execs": cnt[i], "lanes": lanes[i]}
                                   for i, name in enumerate(_names(cfg)) if cnt[i]}}))
+
+
+def live_table(v):
+    """The BVH loop by live lanes (kernel.hip, kLiveRows): per top-level entry class, per bin of
+    lanes still traversing, the wave cycles and iterations of the loop (plain and quad mode), the
+    bvh_hit calls by lanes active at entry, and the share of the loop's cycles at <= 16 lanes."""
+    nb = v["bins"]
+    labels = [str(i + 1) for i in range(16)] + [f"{17 + 4 * i}-{20 + 4 * i}" for i in range(nb - 16)]
+    for c, flat in enumerate(v["classes"]):
+        rows = [flat[r * nb:(r + 1) * nb] for r in range(v["rows"])]
+        cyc, its, qcyc, qits, calls = rows
+        if not (sum(its) + sum(qits) + sum(calls)):
+            continue
+        tot = sum(cyc) + sum(qcyc)
+        name = f"entry {c}" if c < len(v["classes"]) - 1 else f"entries {c}+"
+        print(f"live lanes, {name}: loop cycles {tot}, at <= 16 lanes {sum(cyc[:16]) / max(tot, 1):.4f} plain + "
+              f"{sum(qcyc) / max(tot, 1):.4f} quad, at <= 8 lanes {sum(cyc[:8]) / max(tot, 1):.4f} plain; "
+              f"calls {sum(calls)}")
+        print(f"{'lanes':>7s} {'cycles':>14s} {'cyc%':>6s} {'iterations':>11s} {'cyc/it':>7s} {'quad cycles':>13s} "
+              f"{'quad its':>10s} {'cyc/it':>7s} {'calls':>10s}")
+        for b in range(nb):
+            if cyc[b] + qcyc[b] + calls[b] == 0:
+                continue
+            print(f"{labels[b]:>7s} {cyc[b]:14d} {100 * cyc[b] / max(tot, 1):6.2f} {its[b]:11d} "
+                  f"{cyc[b] / max(its[b], 1):7.0f} {qcyc[b]:13d} {qits[b]:10d} {qcyc[b] / max(qits[b], 1):7.0f} "
+                  f"{calls[b]:10d}")
 
 
 def _names(cfg):
